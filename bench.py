@@ -127,6 +127,46 @@ def _live_traffic(want_prefix, args):
                                                           f"correction) + --pmc WRITE_SIZE ({vals['WRITE_SIZE'][1]} launches), separate passes of this script")
 
 
+DUMP_BUDGET_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+DUMP_FULL_ELEMS = 1 << 20             # tensors up to this size are written whole; larger ones as a fixed, seeded sample of this many
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, store, losses, grad_norm):
+    """What a caller of the timed path receives after its last step, as float32 .npy files under ``out_dir``: every loss of that step
+    (``loss_<name>``), its pre-clip global gradient norm (``grad_norm``), and the updated parameters / BatchNorm statistics (``<state key>``;
+    integer step counters are skipped).  A tensor larger than DUMP_FULL_ELEMS is written as the elements at a fixed set of flat
+    indices (sorted; drawn from a CPU generator seeded with DUMP_SEED and the key, so every run and every build picks the same ones).
+    Returns {name: number of elements written}."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+
+    def put(name, arr):
+        nonlocal total
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+        if total + arr.nbytes > DUMP_BUDGET_BYTES:
+            raise RuntimeError(f"--dump-outputs: {name} would take the dump past {DUMP_BUDGET_BYTES} bytes")
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+        written[name] = int(arr.size)
+
+    for k, v in losses.items():
+        put(f"loss_{k}", np.array([v]))
+    put("grad_norm", np.array([grad_norm]))
+    for k, t in store.state_dict(device=store.device).items():
+        if not t.is_floating_point():
+            continue
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_FULL_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SEED + zlib.crc32(k.encode()))
+            idx = torch.randint(0, flat.numel(), (DUMP_FULL_ELEMS,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        put(k, flat.float().cpu().numpy())
+    return written
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,8 +182,11 @@ def parse():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--features", type=int, default=0, help="override the per-layer feature count (shape experiments; "
                     "the headline metric is quoted on the default)")
-    ap.add_argument("--repeats", type=int, default=25, help="after the timed region: this many more windows of --steps steps, "
-                    "reported as median / min / max (0 = skip)")
+    ap.add_argument("--repeats", type=int, default=0, help="this many MORE timed windows of --steps steps after the first, `value` and "
+                    "`ms_per_step` then the median window (default 0: exactly --steps timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its "
+                    "last step (losses, grad norm, updated parameters; large tensors as a fixed seeded sample) as DIR/<name>.npy, float32, "
+                    "at most 64 MB in all")
     ap.add_argument("--no-other", action="store_true", help="skip the short legs of the other BASELINE configs / modes")
     ap.add_argument("--dry", action="store_true", help="multi-GPU day-one check instead of the benchmark: cohort broadcast, ONE one-epoch "
                     "trial per rank, all_gather of the records, winner broadcast -- prints the seconds of every phase and each rank's "
@@ -410,9 +453,16 @@ def main():
     losses = pipe.losses()
     finite = all(v == v and abs(v) != float("inf") for v in losses.values())
 
-    # ---- the same window R more times, timed the same way.  `value` is the MEDIAN window (the first one included): one 20-60 step
-    # window is 20-60 ms, within reach of a single clock / power-management event; the first window is printed beside it.
+    # ---- --repeats R: the same window R more times, timed the same way; `value` is then the MEDIAN window (the first one included)
     wins = [first_window] + [window() for _ in range(max(a.repeats, 0))]
+    if a.repeats > 0:
+        losses = pipe.losses()
+        finite = all(v == v and abs(v) != float("inf") for v in losses.values())
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # (before anything below steps the model again: the roofline leg re-issues the tapes eagerly)
+        torch.cuda.synchronize()
+        dumped = dump_outputs(a.dump_outputs, store, losses, float(store.ctrl[5]))
     srt = sorted(wins)
     elapsed = srt[len(srt) // 2]
     repeat_stats = {"windows": len(wins), "steps_per_window": a.steps, "first_window_ms_per_step": round(1e3 * first_window / a.steps, 4),
@@ -602,6 +652,8 @@ def main():
                        "loss_finite": finite, "last_losses": {k: round(v, 6) for k, v in losses.items()}},
             "roofline": roof, "cpu_baseline": cpu, "repeat_stats": repeat_stats, "other": other, "sweep": sweep,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "files": len(dumped), "elements": sum(dumped.values())}
         if use_pg:
             # north_star's N-GPU figure is the SHARDED SWEEP's aggregate (`value` above is N independent fits: weak scaling by
             # construction); `sweep_scaling` = that aggregate over the N = 1 sweep leg's (--n1-sweep, or this round's committed line)

@@ -962,7 +962,8 @@ class StepPlan:
         self.dev = store.device
         self._ws = [Workspace(self.dev)]
         self._branch = 0
-        self.branches = bool(branches) and os.environ.get("FX_BRANCHES", "1") != "0"   # per-modality chains as parallel hipGraph branches
+        self.branches = (bool(branches) and os.environ.get("FX_BRANCHES", "1") != "0"   # per-modality chains as parallel hipGraph branches
+                         and ops.hw_queues() >= ops.MIN_HW_QUEUES_FOR_BRANCHES)          # (not on fewer hardware queues: see ops.py)
         # FX_BN_SLABS=1 folds the reduction of the wide layer's partial sums (+ bias) into the BatchNorm kernel (one launch
         # less per wide layer).  Measured twice, no gain: 1.289 vs 1.276 ms/step at cfg2 with the fused next-step forward
         # (the BatchNorm kernel then re-reads 6 slabs instead of one array), so it stays an A/B switch.

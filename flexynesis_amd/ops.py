@@ -143,6 +143,20 @@ def release_thread_streams():
             del _POOLS[key]
 
 
+def hw_queues() -> int:
+    """Hardware queues the HIP runtime maps this process's streams onto per device: GPU_MAX_HW_QUEUES, else the runtime's default 4."""
+    try:
+        return int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+    except ValueError:
+        return 4
+
+
+# The step graphs' parallel branches (per modality / per decoder, with their cross-branch events) were built and measured on the
+# runtime's 4 hardware queues.  With fewer, graph branches share in-order queues: such graphs hang, and the VAE step graph crashes
+# inside hipGraphLaunch.  Below this many queues the plans issue every segment on one stream (the same launches in a valid order).
+MIN_HW_QUEUES_FOR_BRANCHES = 4
+
+
 def side_streams(n: int, group: int = 0) -> List["torch.cuda.Stream"]:
     import threading
     # one pool per (device, host thread): trials in flight on several threads (trials.run_units(in_flight=...)) must not share

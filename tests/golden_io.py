@@ -142,3 +142,53 @@ class FinetuneLoopGolden:
     def unit(self, unit):
         t = self.tag(unit)
         return float(self.z[t + "/val_loss"]), int(self.z[t + "/stopped_epoch"]), [float(x) for x in self.z[t + "/val_losses"]]
+
+
+# ---- recorded reference results (tests/golden/reference/<name>.npz) --------------------------------------------------------
+# The pinning tests compare the restatement with what the reference's own classes compute.  The reference's side of each
+# comparison is recorded here, so the tests need nothing outside the repository; FX_RECORD_REFERENCE=1 re-runs it (only where
+# the reference is importable, oracle/ref_shim.py) and rewrites the file.  Values keep their kind: torch tensors come back as
+# tensors, numpy arrays as arrays, strings / numbers / None / lists / dicts (string keys) as themselves (tuples as lists).
+RECORD_DIR = os.path.join(GOLDEN_DIR, "reference")
+RECORD_ENV = "FX_RECORD_REFERENCE"
+
+
+def _pack(obj, arrays):
+    if isinstance(obj, dict):
+        assert all(isinstance(k, str) for k in obj), list(obj)
+        return {"d": [[k, _pack(v, arrays)] for k, v in obj.items()]}
+    if isinstance(obj, (list, tuple)):
+        return {"l": [_pack(v, arrays) for v in obj]}
+    if obj is None or isinstance(obj, (str, bool, int, float)):
+        return {"v": obj}
+    if isinstance(obj, torch.Tensor):
+        arrays.append(obj.detach().cpu().numpy())
+        return {"t": len(arrays) - 1}
+    if isinstance(obj, (np.ndarray, np.generic)):
+        arrays.append(np.asarray(obj))
+        return {"a": len(arrays) - 1}
+    raise TypeError(f"cannot record a {type(obj).__name__}")
+
+
+def _unpack(m, z):
+    if "d" in m:
+        return {k: _unpack(v, z) for k, v in m["d"]}
+    if "l" in m:
+        return [_unpack(v, z) for v in m["l"]]
+    if "v" in m:
+        return m["v"]
+    if "t" in m:
+        return torch.from_numpy(np.array(z[f"a{m['t']}"]))
+    return np.array(z[f"a{m['a']}"])
+
+
+def recorded(name, make):
+    """The reference's result `make()` as recorded in tests/golden/reference/<name>.npz (re-recorded under FX_RECORD_REFERENCE=1)."""
+    path = os.path.join(RECORD_DIR, name + ".npz")
+    if os.environ.get(RECORD_ENV) == "1":
+        arrays = []
+        manifest = _pack(make(), arrays)
+        os.makedirs(RECORD_DIR, exist_ok=True)
+        np.savez_compressed(path, manifest=np.array(json.dumps(manifest)), **{f"a{i}": a for i, a in enumerate(arrays)})
+    with np.load(path, allow_pickle=False) as z:
+        return _unpack(json.loads(str(z["manifest"])), z)

@@ -1,7 +1,7 @@
 """flexynesis_amd.adapters without a GPU: the adapter functions carry the reference's signatures and read only attributes the
-reference's classes really set (checked against the reference's source where it exists -- the build container; the source is
-parsed, never imported: flexynesis.main sets torch's matmul precision to "medium" at import, main.py:24), and install() replaces
-exactly the two methods + the model classes."""
+reference's classes really set (checked against what parsing the reference's main.py finds -- the argument lists and attribute
+names, recorded in tests/golden/reference/main_interface.npz; the source is parsed, never imported: flexynesis.main sets torch's
+matmul precision to "medium" at import, main.py:24), and install() replaces exactly the two methods + the model classes."""
 import ast
 import inspect
 import os
@@ -9,7 +9,7 @@ import types
 
 import pytest
 
-REF_MAIN = "/root/reference/flexynesis/main.py"
+from golden_io import recorded
 
 
 def _self_attrs(fn_src, name="self"):
@@ -24,11 +24,11 @@ def test_adapter_signatures_are_the_references():
     assert list(inspect.signature(adapters.run_experiments).parameters) == ["self"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_MAIN), reason="the reference exists in the build container only")
-def test_adapters_read_only_what_the_reference_classes_set():
-    import textwrap
-    from flexynesis_amd import adapters
-    tree = ast.parse(open(REF_MAIN).read())
+def _reference_main_interface():
+    """Names only: the argument lists of HyperparameterTuning.objective / FineTuner.run_experiments, the attributes the two classes'
+    __init__ assign on self, and the attributes of self the reference's objective reads."""
+    from oracle import ref_shim
+    tree = ast.parse(open(os.path.join(ref_shim.REFERENCE_ROOT, "flexynesis", "main.py")).read())
     classes = {n.name: n for n in tree.body if isinstance(n, ast.ClassDef)}
 
     def method(cls, name):
@@ -36,18 +36,29 @@ def test_adapters_read_only_what_the_reference_classes_set():
 
     def assigned_in_init(cls):
         init = method(cls, "__init__")
-        return {t.attr for n in ast.walk(init) if isinstance(n, ast.Assign) for t in n.targets
-                if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == "self"}
-    # the reference's own signatures
+        return sorted({t.attr for n in ast.walk(init) if isinstance(n, ast.Assign) for t in n.targets
+                       if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == "self"})
     ref_obj = method("HyperparameterTuning", "objective")
-    assert [a.arg for a in ref_obj.args.args] == ["self", "params", "current_step", "total_steps", "full_train"]
-    assert [a.arg for a in method("FineTuner", "run_experiments").args.args] == ["self"]
+    return {"objective_args": [a.arg for a in ref_obj.args.args],
+            "run_experiments_args": [a.arg for a in method("FineTuner", "run_experiments").args.args],
+            "hp_init_sets": assigned_in_init("HyperparameterTuning"), "ft_init_sets": assigned_in_init("FineTuner"),
+            "objective_reads": sorted({n.attr for n in ast.walk(ref_obj)
+                                       if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "self"})}
+
+
+def test_adapters_read_only_what_the_reference_classes_set():
+    import textwrap
+    from flexynesis_amd import adapters
+    ref = recorded("main_interface", _reference_main_interface)
+    # the reference's own signatures
+    assert ref["objective_args"] == ["self", "params", "current_step", "total_steps", "full_train"]
+    assert ref["run_experiments_args"] == ["self"]
     # every attribute the adapters READ is one the reference's __init__ sets
-    hp_set, ft_set = assigned_in_init("HyperparameterTuning"), assigned_in_init("FineTuner")
+    hp_set, ft_set = set(ref["hp_init_sets"]), set(ref["ft_init_sets"])
     obj_reads = _self_attrs(textwrap.dedent(inspect.getsource(adapters.objective)))
     assert obj_reads <= hp_set, obj_reads - hp_set
     # ... and the adapter reads everything of the configuration the reference's objective reads (loader / progress-bar plumbing aside)
-    ref_reads = {n.attr for n in ast.walk(ref_obj) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "self"}
+    ref_reads = set(ref["objective_reads"])
     plumbing = {"DataLoader", "loader_dataset", "num_workers", "setup_trainer"}
     assert ref_reads - plumbing <= obj_reads, (ref_reads - plumbing) - obj_reads
     ft_reads = _self_attrs(textwrap.dedent(inspect.getsource(adapters.run_experiments)))

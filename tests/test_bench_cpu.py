@@ -57,3 +57,34 @@ def test_main_self_launches_only_without_a_launcher(monkeypatch):
     except SystemExit as e:
         assert "WORLD_SIZE=2" in str(e.code)
     assert calls == [4]
+
+
+def test_dump_outputs_writes_float32_files_within_the_budget(tmp_path):
+    """--dump-outputs: losses, grad norm and the float state as DIR/<name>.npy (float32); a tensor above DUMP_FULL_ELEMS as the same
+    seeded sample of its elements on every call; integer buffers skipped; the total stays under DUMP_BUDGET_BYTES."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class Store:
+        device = torch.device("cpu")
+
+        def state_dict(self, device="cpu"):
+            g = torch.Generator().manual_seed(0)
+            return {"w.big": torch.randn(b.DUMP_FULL_ELEMS + 12345, generator=g), "w.small": torch.randn(3, 4, generator=g),
+                    "bn.num_batches_tracked": torch.tensor(5)}
+
+    got = {}
+    for run in ("a", "b"):
+        d = tmp_path / run
+        written = b.dump_outputs(str(d), Store(), {"total": 1.5, "y": 0.25}, 3.0)
+        assert sorted(written) == ["grad_norm", "loss_total", "loss_y", "w.big", "w.small"]
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert all(a.dtype == np.float32 for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= b.DUMP_BUDGET_BYTES
+        got[run] = files
+    big = Store().state_dict()["w.big"].numpy()
+    assert got["a"]["w.big.npy"].shape == (b.DUMP_FULL_ELEMS,) and np.isin(got["a"]["w.big.npy"], big).all()
+    assert np.array_equal(got["a"]["w.big.npy"], got["b"]["w.big.npy"])            # the same sample every time
+    assert np.array_equal(got["a"]["w.small.npy"], Store().state_dict()["w.small"].numpy().reshape(-1))
+    assert got["a"]["loss_y.npy"].tolist() == [0.25] and got["a"]["grad_norm.npy"].tolist() == [3.0]

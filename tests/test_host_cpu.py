@@ -121,13 +121,14 @@ def test_triplet_dataset_index_semantics_match_reference_golden():
 
 @pytest.mark.parametrize("name,targets", [("DirectPred", ["y", "c"]), ("supervised_vae", ["c"]),
                                           ("MultiTripletNetwork", ["c", "y"])])
-def test_model_class_api_surface(name, targets):
+def test_model_class_api_surface(name, targets, monkeypatch):
     import flexynesis_amd.models as M
+    monkeypatch.setenv("FX_TORCH_ADAM", "1")      # configure_optimizers' torch.optim.Adam (what it returns without a GPU) on any machine
     cls = getattr(M, name)
     ds = _toy_dataset(missing_label=True)
     cfg = {"latent_dim": 8, "hidden_dim_factor": 0.25, "lr": 1e-3, "supervisor_hidden_dim": 4, "epochs": 2,
            "batch_size": 8}
-    m = cls(cfg, ds, targets, surv_event_var="event", surv_time_var="time")
+    m = cls(cfg, ds, targets, surv_event_var="event", surv_time_var="time", device_type="cpu")
     assert cls.__name__ == name
     assert m.target_variables == targets + ["event"] and m.variables == m.target_variables
     assert m.config is cfg and m.surv_event_var == "event" and m.feature_importances == {}
@@ -376,32 +377,43 @@ def test_triplet_sampler_rejects_what_the_reference_cannot_sample():
     assert pos.tolist() == [1, 0, 1, 0] and neg.tolist() == [2, 2, 2, 2]
 
 
-@pytest.mark.skipif(not __import__("oracle.ref_shim", fromlist=["x"]).available(), reason="reference only exists in the build container")
 def test_triplet_sampler_matches_the_reference_dataset_distribution():
-    """Live: the reference's TripletMultiOmicDataset.__getitem__ (numpy / random RNG) and the device sampler draw from the
-    same distribution -- per anchor, the empirical frequencies of every (positive, negative) index agree within 5 sigma."""
-    import random
-    from oracle import ref_shim
+    """The reference's TripletMultiOmicDataset.__getitem__ (numpy / random RNG; its draws recorded in
+    tests/golden/reference/triplet_draws.npz) and the device sampler draw from the same distribution -- per anchor, the empirical
+    frequencies of every (positive, negative) index agree within 5 sigma."""
+    from golden_io import recorded
     from flexynesis_amd.fit import TripletSampler
-    R = ref_shim.load()
     lab = _triplet_labels()
     n = lab.numel()
-    dat = {"a": torch.arange(n, dtype=torch.float32).reshape(n, 1)}           # the feature IS the sample index
-    ds = R.MultiOmicDataset(dat, {"c": lab}, {"c": "categorical"}, {"a": ["f"]}, [f"s{i}" for i in range(n)], {})
-    tds = R.TripletMultiOmicDataset(ds, "c")
-    sm = TripletSampler(lab)
-    assert tds.valid_indices == sm.valid.tolist()
-    np.random.seed(0)
-    random.seed(0)
     reps = 3000
+
+    def reference():
+        import random
+        from oracle import ref_shim
+        R = ref_shim.load()
+        dat = {"a": torch.arange(n, dtype=torch.float32).reshape(n, 1)}           # the feature IS the sample index
+        ds = R.MultiOmicDataset(dat, {"c": lab}, {"c": "categorical"}, {"a": ["f"]}, [f"s{i}" for i in range(n)], {})
+        tds = R.TripletMultiOmicDataset(ds, "c")
+        np.random.seed(0)
+        random.seed(0)
+        pos, neg = [], []
+        for ai, a in enumerate(tds.valid_indices):
+            ref_pos, ref_neg = torch.zeros(n), torch.zeros(n)
+            for _ in range(reps):
+                anc, p, ng, y = tds[ai]
+                assert int(anc["a"].item()) == a
+                ref_pos[int(p["a"].item())] += 1
+                ref_neg[int(ng["a"].item())] += 1
+            pos.append(ref_pos)
+            neg.append(ref_neg)
+        return {"valid_indices": [int(i) for i in tds.valid_indices], "pos": torch.stack(pos), "neg": torch.stack(neg)}
+    R = recorded("triplet_draws", reference)
+    sm = TripletSampler(lab)
+    assert R["valid_indices"] == sm.valid.tolist()
     gen = torch.Generator().manual_seed(1)
-    for ai, a in enumerate(tds.valid_indices):
-        ref_pos, ref_neg = torch.zeros(n), torch.zeros(n)
-        for _ in range(reps):
-            anc, p, ng, y = tds[ai]
-            assert int(anc["a"].item()) == a
-            ref_pos[int(p["a"].item())] += 1
-            ref_neg[int(ng["a"].item())] += 1
+    for ai, a in enumerate(R["valid_indices"]):
+        ref_pos, ref_neg = R["pos"][ai], R["neg"][ai]
+        assert float(ref_pos.sum()) == reps and float(ref_neg.sum()) == reps
         p2, n2 = sm.sample(torch.full((reps,), a), gen)
         got_pos, got_neg = torch.bincount(p2, minlength=n).float(), torch.bincount(n2, minlength=n).float()
         for ref, got in ((ref_pos, got_pos), (ref_neg, got_neg)):
@@ -438,33 +450,36 @@ def test_model_builds_from_the_inference_namespace():
         assert sd[first].shape == (20, 40)
 
 
-@pytest.mark.skipif(not __import__("oracle.ref_shim", fromlist=["x"]).available(), reason="reference only exists in the build container")
 @pytest.mark.parametrize("name", ["DirectPred", "supervised_vae", "MultiTripletNetwork", "CrossModalPred"])
 def test_state_dict_loads_into_the_reference_model(name):
-    """The other direction of the checkpoint ABI: a state_dict produced by the engine's model class loads STRICTLY into
-    the reference's class (same keys, shapes and dtypes, incl. the int64 num_batches_tracked buffers), so weights trained
-    here can be handed to the reference's inference / attribution code."""
+    """The other direction of the checkpoint ABI: a state_dict produced by the engine's model class has exactly the keys, shapes and
+    dtypes of the reference's class (incl. the int64 num_batches_tracked buffers; the reference's recorded in
+    tests/golden/reference/ref_state_layout_*.npz), i.e. it loads STRICTLY into it, so weights trained here can be handed to the
+    reference's inference / attribution code."""
     import flexynesis_amd.models as M
-    from oracle import ref_capture, ref_shim
+    from golden_io import recorded
     from oracle import restate as O
     from oracle.gen_goldens import make_cohort
-    R = ref_shim.load()
     kw = dict(input_layers=["a"], output_layers=["b", "a"]) if name == "CrossModalPred" else {}
     spec = O.Spec(name, [("a", 30), ("b", 18)], 6, 0.4, 3, [("c", "categorical", 3), ("y", "numerical", 1)], **kw)
     dat, ann, vt = make_cohort(spec, 30, seed=2, missing=False)
     cfg = {"latent_dim": 6, "hidden_dim_factor": 0.4, "lr": 1e-3, "supervisor_hidden_dim": 3, "epochs": 1, "batch_size": 6}
-    ref = ref_capture.build_reference_model(R, spec, ref_capture.make_dataset(R, dat, ann, vt), cfg)
+
+    def reference():
+        from oracle import ref_capture, ref_shim
+        R = ref_shim.load()
+        ref = ref_capture.build_reference_model(R, spec, ref_capture.make_dataset(R, dat, ann, vt), cfg)
+        return {k: {"shape": list(v.shape), "dtype": str(v.dtype)} for k, v in ref.state_dict().items()}
+    layout = recorded(f"ref_state_layout_{name}", reference)
     from flexynesis_amd.data import MultiOmicDataset
     ds = MultiOmicDataset(dat, ann, vt, {k: [f"{k}_{j}" for j in range(v.shape[1])] for k, v in dat.items()},
                           [f"s{i}" for i in range(30)], {})
     torch.manual_seed(5)
     mine = getattr(M, name)(cfg, ds, ["c", "y"], device_type="cpu", **kw)
     sd = mine.state_dict()
-    sd["encoders.0." + ("layer_1" if name in ("DirectPred", "MultiTripletNetwork") else "hidden_layers.0") + ".weight"] += 0.25
-    res = ref.load_state_dict(sd, strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    for k, v in ref.state_dict().items():
-        assert v.dtype == sd[k].dtype and torch.equal(v, sd[k]), k
+    assert sorted(sd) == sorted(layout), set(sd) ^ set(layout)                 # strict: no missing, no unexpected keys
+    for k, v in sd.items():
+        assert list(v.shape) == layout[k]["shape"] and str(v.dtype) == layout[k]["dtype"], (k, v.shape, v.dtype, layout[k])
 
 
 def test_fused_level1_mode_is_chosen_only_under_a_suitable_trainer():

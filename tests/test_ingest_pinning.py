@@ -1,14 +1,14 @@
 """Pin the ingest restatement (oracle/ingest_restate.py) against the fixtures generated from the reference's own
 DataImporter methods (tests/golden/ingest_*.npz, oracle/gen_ingest_goldens.py), against pandas / scikit-learn (the
-un-vendored dependencies whose arithmetic it restates) and -- when /root/reference is present -- against the reference
-itself on fresh seeds.  CPU only."""
+un-vendored dependencies whose arithmetic it restates) and against the reference itself on fresh seeds (its results
+recorded in tests/golden/reference/ingest_live_*.npz, golden_io.recorded).  CPU only."""
 import os
 
 import numpy as np
 import pytest
 
+from golden_io import recorded
 from oracle import ingest_restate as R
-from oracle import ref_shim
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = ["ingest_f64", "ingest_f32", "ingest_f64_log", "ingest_f32_log"]
@@ -88,13 +88,12 @@ def test_harmonize_keeps_training_order():
     assert a.tolist() == [0, 2, 3] and b.tolist() == [1, 3, 0]
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference not present (GPU box)")
 @pytest.mark.parametrize("seed,dtype,logt", [(101, np.float64, False), (102, np.float32, False), (103, np.float64, True),
                                              (104, np.float32, True)])
 def test_restatement_matches_live_reference(seed, dtype, logt):
     from oracle import gen_ingest_goldens as G
     feats = [("a", 60), ("b", 45)]
     train, test = G.make_case(seed, 33, 14, feats, dtype, counts=logt)
-    exp = G.reference_import(train, test, 0.02, 0.2, logt)
+    exp = recorded(f"ingest_live_{seed}", lambda: G.reference_import(train, test, 0.02, 0.2, logt))
     out = R.import_matrices(train, test, variance_threshold=0.02, na_threshold=0.2, log_transform=logt)
     check_against(out, exp, [k for k, _ in feats], exact=True)

@@ -1,13 +1,13 @@
 """Pin the CPU restatement (oracle/restate.py) against the golden vectors generated from the
-reference (tests/golden/, oracle/gen_goldens.py) and -- when /root/reference is present -- against
-the reference itself, live.  CPU only."""
+reference (tests/golden/, oracle/gen_goldens.py) and against the reference's own classes on fresh shapes (their results
+recorded in tests/golden/reference/, golden_io.recorded).  CPU only."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import restate as O
 from oracle import ref_shim
-from golden_io import Golden, MODEL_CASES
+from golden_io import Golden, MODEL_CASES, recorded
 
 RTOL, ATOL = 2e-5, 2e-6
 
@@ -148,12 +148,26 @@ def test_function_goldens():
     close(O.total_loss(spec, st, {"y": tot["l1"]}, True), tot["single"], what="single-term total")
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference only exists in the build container")
-def test_live_reference_step_matches_oracle():
-    """Fresh shapes/seeds (not the committed goldens): reference vs restatement, one step each model."""
+def _reference_steps(spec, dat, ann, vt, batches, **kw):
+    """The reference's own model class through ref_capture.reference_train_steps from perturbed_state(seed=3): per step the loss,
+    the draws, the gradients, the clip norm and the state after the step."""
     from oracle import ref_capture
-    from oracle.gen_goldens import make_cohort, make_batches, perturbed_state
+    from oracle.gen_goldens import perturbed_state
     R = ref_shim.load()
+    ds = ref_capture.make_dataset(R, dat, ann, vt)
+    cfg = {"latent_dim": spec.latent_dim, "hidden_dim_factor": spec.hidden_dim_factor, "lr": 3e-3,
+           "supervisor_hidden_dim": spec.supervisor_hidden_dim, "epochs": 1, "batch_size": 6}
+    model = ref_capture.build_reference_model(R, spec, ds, cfg)
+    model.load_state_dict(perturbed_state(spec, seed=3))
+    recs = ref_capture.reference_train_steps(R, spec, model, batches, 3e-3, **kw)
+    return [{"total": r.total, "draws": r.draws, "grads": r.grads, "grad_norm": r.grad_norm, "state": r.state} for r in recs]
+
+
+def test_live_reference_step_matches_oracle():
+    """Fresh shapes/seeds (not the committed goldens): reference vs restatement, one step each model (the reference's side recorded
+    in tests/golden/reference/live_step_*.npz)."""
+    from types import SimpleNamespace
+    from oracle.gen_goldens import make_cohort, make_batches, perturbed_state
     specs = [
         O.Spec("DirectPred", [("a", 33), ("b", 21)], 5, 0.4, 3, [("c", "categorical", 4), ("y", "numerical", 1)]),
         O.Spec("supervised_vae", [("a", 30), ("b", 18)], 6, 0.3, 3, [("y", "numerical", 1)]),
@@ -165,16 +179,12 @@ def test_live_reference_step_matches_oracle():
         O.Spec("CrossModalPred", [("a", 30), ("b", 18), ("d", 22)], 6, 0.3, 3, [], input_layers=["a", "b"],
                output_layers=["d", "a"]),
     ]
-    for spec in specs:
+    for i, spec in enumerate(specs):
         dat, ann, vt = make_cohort(spec, 30, seed=9, missing=False)
-        ds = ref_capture.make_dataset(R, dat, ann, vt)
-        cfg = {"latent_dim": spec.latent_dim, "hidden_dim_factor": spec.hidden_dim_factor, "lr": 3e-3,
-               "supervisor_hidden_dim": spec.supervisor_hidden_dim, "epochs": 1, "batch_size": 6}
-        model = ref_capture.build_reference_model(R, spec, ds, cfg)
         st0 = perturbed_state(spec, seed=3)
-        model.load_state_dict(st0)
         batches = make_batches(spec, dat, ann, 6, 2, seed=4, missing=False)
-        recs = ref_capture.reference_train_steps(R, spec, model, batches, 3e-3)
+        recs = [SimpleNamespace(**r) for r in
+                recorded(f"live_step_{i}_{spec.model}", lambda: _reference_steps(spec, dat, ann, vt, batches))]
         st, opt = st0, {}
         for si, (b, r) in enumerate(zip(batches, recs)):
             st, opt, info = O.train_step(spec, st, opt, b, r.draws, 3e-3)
@@ -185,26 +195,22 @@ def test_live_reference_step_matches_oracle():
                           what=f"{spec.model} {k}")
 
 
-@pytest.mark.skipif(not ref_shim.available(), reason="reference only exists in the build container")
 @pytest.mark.parametrize("freeze", [{"encoders": True, "supervisors": False}, {"encoders": False, "supervisors": True}])
 def test_live_reference_finetune_step_matches_oracle(freeze):
     """FineTuner steps (reference main.py:530-539, :562-566, :591-600): frozen parameter groups, Adam over the
-    trainable ones, NO gradient clipping -- reference vs the restatement's train_step(clip=False, frozen=...)."""
-    from oracle import ref_capture
+    trainable ones, NO gradient clipping -- reference (recorded in tests/golden/reference/live_finetune_*.npz) vs the
+    restatement's train_step(clip=False, frozen=...)."""
+    from types import SimpleNamespace
     from oracle.gen_goldens import make_cohort, make_batches, perturbed_state
-    R = ref_shim.load()
     frozen = tuple(p for p, on in (("encoders.", freeze["encoders"]), ("MLPs.", freeze["supervisors"])) if on)
+    tag = "enc_frozen" if freeze["encoders"] else "sup_frozen"
     for spec in (O.Spec("DirectPred", [("a", 33), ("b", 21)], 5, 0.4, 3, [("c", "categorical", 4), ("y", "numerical", 1)]),
                  O.Spec("supervised_vae", [("a", 30), ("b", 18)], 6, 0.3, 3, [("y", "numerical", 1)])):
         dat, ann, vt = make_cohort(spec, 30, seed=9, missing=False)
-        ds = ref_capture.make_dataset(R, dat, ann, vt)
-        cfg = {"latent_dim": spec.latent_dim, "hidden_dim_factor": spec.hidden_dim_factor, "lr": 3e-3,
-               "supervisor_hidden_dim": spec.supervisor_hidden_dim, "epochs": 1, "batch_size": 6}
-        model = ref_capture.build_reference_model(R, spec, ds, cfg)
         st0 = perturbed_state(spec, seed=3)
-        model.load_state_dict(st0)
         batches = make_batches(spec, dat, ann, 6, 2, seed=4, missing=False)
-        recs = ref_capture.reference_train_steps(R, spec, model, batches, 3e-3, clip=False, freeze=freeze)
+        recs = [SimpleNamespace(**r) for r in recorded(f"live_finetune_{tag}_{spec.model}",
+                                                       lambda: _reference_steps(spec, dat, ann, vt, batches, clip=False, freeze=freeze))]
         st, opt = st0, {}
         for si, (b, r) in enumerate(zip(batches, recs)):
             st, opt, info = O.train_step(spec, st, opt, b, r.draws, 3e-3, clip=False, frozen=frozen)
